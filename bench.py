@@ -442,6 +442,33 @@ def trained_cer(device) -> dict:
     return out
 
 
+def dump_outputs(out_dir: str, gathered: list, compared: list, merged: list) -> None:
+    """--dump-outputs: what the timed path handed its caller in its last timed step, as float arrays that two builds of the project
+    can be compared with (the inputs are seeded, so the same arguments give the same inputs).  Token ids and code points are below
+    2^24, exact in float32; the whole dump is a few MB at the default shape (<= 256 reads x 512 tokens per rank).
+        tokens.npy             [reads of every rank, new_tokens]  greedy token streams, rank-major (the gather on rank 0)
+        token_counts.npy       [reads of every rank]              stream lengths the gather carried
+        merged_text.npy        [pages, max_len]                   merge_versions of each page of rank 0, code points, -1 padded
+        merged_len.npy         [pages]                            their lengths
+        compare_versions.npy   [pages, 3]                         agreement_rate, char_edit_distance, word_edit_distance of
+                                                                  reads 1 and 2 of each page of rank 0 (absent with --reads 1)"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"tokens": np.concatenate([t.cpu().numpy() for t, _ in gathered]).astype(np.float32),
+              "token_counts": np.concatenate([c.cpu().numpy() for _, c in gathered]).astype(np.float32),
+              "merged_len": np.asarray([len(m) for m in merged], np.float32)}
+    codes = np.full((len(merged), max([len(m) for m in merged] + [1])), -1.0, np.float32)
+    for i, m in enumerate(merged):
+        codes[i, : len(m)] = [ord(ch) for ch in m]
+    arrays["merged_text"] = codes
+    if compared:
+        arrays["compare_versions"] = np.asarray([[c["agreement_rate"], c["char_edit_distance"], c["word_edit_distance"]]
+                                                 for c in compared], np.float64)
+    if sum(a.nbytes for a in arrays.values()) > 64 << 20:
+        raise SystemExit(f"--dump-outputs: {sum(a.nbytes for a in arrays.values())} bytes exceed the 64 MB bound")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(n: int, argv: list[str]) -> int:
     """`python bench.py --gpus N` without a launcher: start N copies of this script, one per GPU, with the rendezvous
     variables torch.distributed.run would set, wait, and relay rank 0's JSON line.  This parent makes no GPU call (a
@@ -515,7 +542,11 @@ def main() -> None:
                          "beside batch k+1's tower + prefill, enforced by events (measured slower: pipeline.py)")
     ap.add_argument("--fp8", action="store_true",
                     help="E4M3 wide GEMMs for the vision tower and the prefill (BASELINE config 4; not the headline configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -564,20 +595,24 @@ def main() -> None:
     # order WHILE the lanes read the next steps (inside the timed region, as with one GPU, where the lane threads merge)
     import threading
     deferred, deferred_cv = {}, threading.Condition()
+    # --dump-outputs: (gathered token streams, compare_versions results, merged texts) of step `record["j"]` of the timed run_steps
+    record = {"j": None, "out": None}
 
-    def gather_and_merge(toks, n_pages):
+    def gather_and_merge(toks, n_pages, j=None):
         t = torch.tensor(toks, dtype=torch.int32, device=dev)
         counts = torch.full((len(toks),), args.new_tokens, dtype=torch.int32, device=dev)
-        shard.gather_token_streams(t, counts, dst=0)
-        merged = []
+        gathered = shard.gather_token_streams(t, counts, dst=0)
+        merged, compared = [], []
         for p in range(n_pages):
             reads = [tok.decode(toks[p * args.reads + r]) for r in range(args.reads)]
             if len(reads) >= 2:
-                text.compare_versions(reads[0], reads[1])
+                compared.append(text.compare_versions(reads[0], reads[1]))
             merged.append(text.merge_versions(reads))
+        if j is not None and j == record["j"] and gathered is not None:
+            record["out"] = (gathered, compared, merged)
         return merged
 
-    def read_and_merge(pages, n_pages, e=None, hooks=None):
+    def read_and_merge(pages, n_pages, e=None, hooks=None, j=None):
         e = e or eng
         toks = e.generate(pages, prompts[: len(pages)], max_new=args.new_tokens, min_new=args.new_tokens, hooks=hooks)
         if hooks is not None and world > 1:
@@ -585,9 +620,9 @@ def main() -> None:
                 deferred[hooks.k] = toks
                 deferred_cv.notify_all()
             return None
-        return gather_and_merge(toks, n_pages)
+        return gather_and_merge(toks, n_pages, j)
 
-    def step(src=None, e=None, hooks=None):
+    def step(src=None, e=None, hooks=None, j=None):
         """One step on engine (lane) e.  src: device-resident raw pages (the timed configuration) or host arrays (upload inside the
         step).  Returns the lane's phase times of this step."""
         e = e or eng
@@ -595,12 +630,12 @@ def main() -> None:
         e0.record()
         pages = [im for raw in (raws_dev if src is None else src) for im in sps[id(e)].pages(raw, strategies, hw)]
         e1.record()
-        read_and_merge(pages, args.pages, e, hooks)
+        read_and_merge(pages, args.pages, e, hooks, j)
         return dict(e.timings, preprocess_ms=e0.elapsed_time(e1))   # (both events long complete: generate synchronised its stream)
 
     def run_steps(k, src=None):
         """k steps through the lanes (lanes == 1: one after the other on this thread's stream): their phase times in step order."""
-        jobs = [(lambda e, hooks, src=src: step(src, e, hooks)) for _ in range(k)]
+        jobs = [(lambda e, hooks, src=src, j=j: step(src, e, hooks, j)) for j in range(k)]
         if world == 1 or len(pipe.engines) == 1 or k <= 1:
             return pipe.run(jobs)
         failed, bad_ranks = [], []
@@ -617,7 +652,7 @@ def main() -> None:
                 if bad:
                     bad_ranks.extend(bad)
                     return
-                gather_and_merge(toks, args.pages)
+                gather_and_merge(toks, args.pages, j)
 
         th = threading.Thread(target=gather_in_step_order, name="hwocr-gather")
         th.start()
@@ -647,10 +682,12 @@ def main() -> None:
     barrier()
     # HIP events around every wide-GEMM launch of the whole timed region (a few microseconds per launch: 0.2 % of a step)
     _lib.check(lib.hwocr_profile_enable(2 if args.fp8 else 1))
+    record["j"] = args.steps - 1 if args.dump_outputs else None
     t0 = time.perf_counter()
     phases = run_steps(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    record["j"] = None   # (the legs below run steps of their own)
     prof_steps, t_prof = args.steps, elapsed
     ms, fl, n = C.c_double(), C.c_double(), C.c_long()
     _lib.check(lib.hwocr_profile_read(C.byref(ms), C.byref(fl), C.byref(n)))
@@ -726,6 +763,8 @@ def main() -> None:
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *record["out"])
 
     pages_total = args.pages * world * args.steps
     value = pages_total / elapsed

@@ -16,7 +16,16 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _cpu_rank():
+    """Called first in every rank these tests spawn: the ranks are CPU processes (gloo, scripted reads), but torch's
+    dist.barrier() probes for an accelerator, which on a GPU host initialises the GPU runtime in each of them — eight ranks
+    beside the test runner are more processes than one shared GPU may have open.  They are told there is none."""
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, q):
+    _cpu_rank()
     os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
                       MASTER_PORT=str(port))
     r, _, w = shard.init_from_env(device_backend=False)
@@ -92,6 +101,7 @@ def _scripted_tokens(images, params=None, on_done=None, long=False):
 
 
 def _folder_worker(rank, world, port, src, out_dir, q, long=False):
+    _cpu_rank()
     import contextlib
     import functools
     import io
@@ -202,6 +212,7 @@ def test_ragged_width_gather_single_process_shapes():
 # A rank whose reads raise must not leave the others waiting in the gather until the backend's timeout: every rank
 # learns who failed (shard.failed_ranks, before the data collective) and every rank leaves with an error, promptly.
 def _failing_folder_worker(rank, world, port, src, out_dir, q):
+    _cpu_rank()
     import contextlib
     import io
     import time

@@ -22,6 +22,7 @@ def fake_engine(monkeypatch):
 
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    monkeypatch.setattr(torch.cuda, "device_count", lambda: 8)  # a node of 8 GPUs, whichever host the test runs on
     monkeypatch.setattr(engine, "ReadEngine", FakeEngine)
     monkeypatch.setattr(engine, "random_state_dict", lambda cfg, seed=0, device="cuda": {"device": device})
     monkeypatch.setattr(tools, "_ocr_model", None)
