@@ -738,7 +738,7 @@ struct DecodeArgs {
   // partials itself (nullptr: attn_decode_merge_kernel does, in a launch of its own)
   int* arrive = nullptr;
   int ahead = 1;  // fused QKV finish: first key block requested before the finish (HWOCR_ATTN_DECODE_AHEAD=0: after, for A/B runs)
-  // E4M3 cache (hwocr_kv.fp8; the KV8 kernel instance): K / VT point at the CODES ([seq][Hkv][ctx * 256 bytes], kv8_k / kv8_v order),
+  // E4M3 cache (hwocr_kv.fp8; the KV8 kernel instances): K / VT point at the CODES ([seq][Hkv][ctx * head_dim bytes], kv8_k / kv8_v order),
   // one scale per token and kv head [seq][Hkv][ctx]
   float* k_scale = nullptr; float* v_scale = nullptr;
 };
@@ -795,11 +795,14 @@ __device__ __forceinline__ void merge_splits(const DecodeArgs& a, int b, int h, 
 // scale multiplies the score, the value scale the softmax weight before it is packed; the appended token is quantised by the
 // workgroup that owns its block.  Gemma's decode attention is 26 % of config 4's kernel time and streams KV at the HBM rate already
 // (1.13 GB per layer at 5.4 TB/s): halving the bytes is what is left.
+// KV8 at head_dim 128 (Qwen2-VL / Qwen2.5-VL): the same operand-order codes (4-KiB blocks: 8 loads of 1 KiB per wave instead of 16),
+// in both geometries of the bf16 128 path - 8 waves, one workgroup per (read, kv head), and 4 waves x nsplit with the merge; the
+// appended token is quantised by waves 0-1 (key) and 2-3 (value) of the owner.
 template <bool TILED, int WAVES, int DEC_HD, int WPE = (DEC_HD == 256 ? 1 : (WAVES == 8 ? 2 : 3)), bool KV8 = false>
 __global__ __launch_bounds__(64 * WAVES, WPE) void attn_decode_kernel(DecodeArgs a) {
   constexpr int KS = DEC_HD / 32, VD = DEC_HD / 16;  // k-steps of the score product, d-tiles of the PV product
   static_assert(!TILED || DEC_HD == 128, "the fragment-tiled cache layout is defined for head_dim 128");
-  static_assert(!KV8 || (DEC_HD == 256 && WAVES == 4 && !TILED), "the E4M3 cache is defined for 256-wide heads (4 waves = one thread per feature)");
+  static_assert(!KV8 || (!TILED && (DEC_HD == 128 || WAVES == 4)), "the E4M3 cache: 256-wide heads on 4 waves (one thread per feature), 128-wide on 4 or 8");
   constexpr int QC = DEC_HD == 256 ? 8 : 16;  // query columns kept for the merge (64 KB static LDS limit): G <= QC
   __shared__ float s_o[WAVES][DEC_HD][QC];
   __shared__ float s_m[WAVES][16];
@@ -916,7 +919,7 @@ __global__ __launch_bounds__(64 * WAVES, WPE) void attn_decode_kernel(DecodeArgs
         kb[TILED ? kv_tiled_k(slot, HALF + i) : (long)slot * DEC_HD + HALF + i] = ob;
       }
     }
-    if constexpr (KV8) {
+    if constexpr (KV8 && DEC_HD == 256) {
       // the owner quantises the new token: thread d holds feature d of k and of v (256 threads, 256 features); scale = max|x| / 448
       // over the token's features (1 for an all-zero row), code = e4m3(x * 448 / max|x|), as hwocr_quant_rows_fp8
       __syncthreads();
@@ -932,11 +935,34 @@ __global__ __launch_bounds__(64 * WAVES, WPE) void attn_decode_kernel(DecodeArgs
         const int vc = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(vx * vinv, -448.0f), 448.0f), 0.f, 0, false);
         unsigned char* K8w = (unsigned char*)a.Kw + reg8 * DEC_HD;
         unsigned char* V8w = (unsigned char*)a.VTw + reg8 * DEC_HD;
-        K8w[kv8_k(slot, tid)] = (unsigned char)(kc & 0xff);
-        V8w[kv8_v(tid, slot)] = (unsigned char)(vc & 0xff);
+        K8w[kv8_k<DEC_HD>(slot, tid)] = (unsigned char)(kc & 0xff);
+        V8w[kv8_v<DEC_HD>(tid, slot)] = (unsigned char)(vc & 0xff);
         if (tid == 0) {
           a.k_scale[reg8 + slot] = kmax > 0.f ? kmax / 448.0f : 1.0f;
           a.v_scale[reg8 + slot] = vmax > 0.f ? vmax / 448.0f : 1.0f;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the appended slot is in L2 before any wave reads it back
+      }
+    } else if constexpr (KV8) {
+      // 128-wide heads: threads 0..127 (waves 0, 1) hold feature tid of k, threads 128..255 (waves 2, 3) feature tid - 128 of v; the
+      // waves of an 8-wave workgroup past the fourth only wait.  Same rule as above.
+      __syncthreads();
+      if (owner) {
+        const bool isv = tid >= DEC_HD, active = tid < 2 * DEC_HD;   // (wave-uniform)
+        const int d = tid & (DEC_HD - 1);
+        const float x = active ? bf2f(isv ? s_row[(a.G + 1) * DEC_HD + d] : s_rot[a.G * DEC_HD + d]) : 0.f;
+        if (active) {
+          const float xm = wave_max(fabsf(x));
+          if (lane == 0) s_m[w][0] = xm;
+        }
+        __syncthreads();
+        if (active) {
+          const float amax = isv ? fmaxf(s_m[2][0], s_m[3][0]) : fmaxf(s_m[0][0], s_m[1][0]);
+          const float inv = amax > 0.f ? 448.0f / amax : 0.f;
+          const int code = __builtin_amdgcn_cvt_pk_fp8_f32(fminf(fmaxf(x * inv, -448.0f), 448.0f), 0.f, 0, false);
+          if (isv) ((unsigned char*)a.VTw + reg8 * DEC_HD)[kv8_v<DEC_HD>(d, slot)] = (unsigned char)(code & 0xff);
+          else ((unsigned char*)a.Kw + reg8 * DEC_HD)[kv8_k<DEC_HD>(slot, d)] = (unsigned char)(code & 0xff);
+          if (d == 0) (isv ? a.v_scale : a.k_scale)[reg8 + slot] = amax > 0.f ? amax / 448.0f : 1.0f;
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the appended slot is in L2 before any wave reads it back
       }
@@ -1197,7 +1223,10 @@ int launch_attn_decode(const DecodeArgs& a, int nseq, int head_dim, hipStream_t 
     if (nsplit > 1 && !a.arrive) hipLaunchKernelGGL(attn_decode_merge_kernel<256>, dim3(a.Hq, nseq), dim3(256), 0, stream, a);
     return hwocr_launch_status();
   }
-  if (nsplit == 1) {
+  if (a.k_scale) {  // E4M3 cache of 128-wide heads: the same two geometries as the bf16 cache
+    if (nsplit == 1) hipLaunchKernelGGL((attn_decode_kernel<false, 8, 128, 2, true>), dim3(1, Hkv, nseq), dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL((attn_decode_kernel<false, 4, 128, 3, true>), dim3(nsplit, Hkv, nseq), dim3(256), 0, stream, a);
+  } else if (nsplit == 1) {
     if (a.kv_tiled) hipLaunchKernelGGL((attn_decode_kernel<true, 8, 128>), dim3(1, Hkv, nseq), dim3(512), 0, stream, a);
     else hipLaunchKernelGGL((attn_decode_kernel<false, 8, 128>), dim3(1, Hkv, nseq), dim3(512), 0, stream, a);
   } else if (a.kv_tiled) {
@@ -1254,12 +1283,13 @@ extern "C" int hwocr_attn_decode_qkv(const float* slabs, int nslab, long slab_st
 }
 
 // the fused step over an E4M3 cache (hwocr.h)
-extern "C" int hwocr_attn_decode_qkv_fp8kv(const float* slabs, int nslab, long slab_stride, const void* bias, void* K8, void* VT8,
-                                           float* k_scale, float* v_scale, const int* lens, const int* rope_delta, const void* cos_tab,
-                                           const void* sin_tab, void* out, float* part_o, float* part_ml, int* arrive, int nseq, int Hq,
-                                           int Hkv, int nsplit, float scale, int ctx, int max_pos, int* status, hipStream_t stream) {
+extern "C" int hwocr_attn_decode_qkv_fp8kv_hd(const float* slabs, int nslab, long slab_stride, const void* bias, void* K8, void* VT8,
+                                              float* k_scale, float* v_scale, const int* lens, const int* rope_delta, const void* cos_tab,
+                                              const void* sin_tab, void* out, float* part_o, float* part_ml, int* arrive, int nseq, int Hq,
+                                              int Hkv, int nsplit, float scale, int ctx, int max_pos, int head_dim, int* status,
+                                              hipStream_t stream) {
   (void)hipGetLastError();
-  if (!attn_decode_args_ok(nseq, Hq, Hkv, nsplit, part_o, part_ml, 0, 0, 0, 0, 0, 256, 0)) return HWOCR_EINVAL;
+  if (!attn_decode_args_ok(nseq, Hq, Hkv, nsplit, part_o, part_ml, 0, 0, 0, 0, 0, head_dim, 0)) return HWOCR_EINVAL;
   if (!slabs || nslab < 1 || !rope_delta || !cos_tab || !sin_tab || ctx < 32 || (ctx % 32) || max_pos < 1 || !K8 || !VT8 || !k_scale || !v_scale)
     return HWOCR_EINVAL;
   DecodeArgs a{nullptr, (const bf16*)K8, (const bf16*)VT8, lens, part_o, part_ml, (bf16*)out, 0, 0, 0, 0, 0, Hq, Hkv, Hq / Hkv, nsplit,
@@ -1268,7 +1298,14 @@ extern "C" int hwocr_attn_decode_qkv_fp8kv(const float* slabs, int nslab, long s
   a.cos_tab = (const bf16*)cos_tab; a.sin_tab = (const bf16*)sin_tab; a.ctx = ctx; a.max_pos = max_pos; a.status = status;
   a.Kw = (bf16*)K8; a.VTw = (bf16*)VT8; a.arrive = arrive; a.k_scale = k_scale; a.v_scale = v_scale;
   a.ahead = 1;
-  return launch_attn_decode(a, nseq, 256, stream);
+  return launch_attn_decode(a, nseq, head_dim, stream);
+}
+extern "C" int hwocr_attn_decode_qkv_fp8kv(const float* slabs, int nslab, long slab_stride, const void* bias, void* K8, void* VT8,
+                                           float* k_scale, float* v_scale, const int* lens, const int* rope_delta, const void* cos_tab,
+                                           const void* sin_tab, void* out, float* part_o, float* part_ml, int* arrive, int nseq, int Hq,
+                                           int Hkv, int nsplit, float scale, int ctx, int max_pos, int* status, hipStream_t stream) {
+  return hwocr_attn_decode_qkv_fp8kv_hd(slabs, nslab, slab_stride, bias, K8, VT8, k_scale, v_scale, lens, rope_delta, cos_tab, sin_tab, out,
+                                        part_o, part_ml, arrive, nseq, Hq, Hkv, nsplit, scale, ctx, max_pos, 256, status, stream);
 }
 
 // the kernel instance hwocr_attn_decode runs for these arguments (for the parity tests' coverage check)

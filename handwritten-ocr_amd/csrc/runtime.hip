@@ -258,8 +258,8 @@ extern "C" int hwocr_prefill(const hwocr_decoder* m, const hwocr_dec_ws* ws, con
       (m->head_dim != 128 && kv->tiled))
     return HWOCR_EINVAL;
   // E4M3 cache (hwocr_kv.fp8): this call's K / V^T stay bf16 in the workspace (ws->kt / ws->vtt: the prefill attention reads them),
-  // then hwocr_kv_quant_fp8 fills the cache
-  if (kv->fp8 && (m->head_dim != 256 || kv->tiled || !kv->k_scale || !kv->v_scale || !ws->kt || !ws->vtt || (kv->ctx % 32))) return HWOCR_EINVAL;
+  // then hwocr_kv_quant_fp8_hd fills the cache (head_dim 256 or 128)
+  if (kv->fp8 && (kv->tiled || !kv->k_scale || !kv->v_scale || !ws->kt || !ws->vtt || (kv->ctx % 32))) return HWOCR_EINVAL;
   const int HD = m->head_dim, G = m->gemma;
   const int rows = nseq * rows_per_seq, Hd = m->hidden, QW = (m->Hq + 2 * m->Hkv) * HD;
   const long k_head = (long)kv->ctx * HD, k_seq = (long)m->Hkv * k_head, k_layer = (long)kv->nseq_max * k_seq;
@@ -289,9 +289,9 @@ extern "C" int hwocr_prefill(const hwocr_decoder* m, const hwocr_dec_ws* ws, con
                              (long)rows_per_seq * m->Hq * HD, (long)m->Hq * HD, scale, kv->tiled, st));
     if (kv->fp8) {  // the cache's share of this layer: codes + one scale per token, for every position of the padded prompt
       const long s_layer = (long)kv->nseq_max * m->Hkv * kv->ctx, s_seq = (long)m->Hkv * kv->ctx;
-      CHECK(hwocr_kv_quant_fp8(Kc, Vc, a_seq, a_head, a_seq, a_head, a_ctx, (unsigned char*)kv->k + l * k_layer + seq0 * k_seq,
-                               (unsigned char*)kv->vt + l * k_layer + seq0 * k_seq, kv->k_scale + l * s_layer + seq0 * s_seq,
-                               kv->v_scale + l * s_layer + seq0 * s_seq, nseq, m->Hkv, rows_per_seq, kv->ctx, st));
+      CHECK(hwocr_kv_quant_fp8_hd(Kc, Vc, a_seq, a_head, a_seq, a_head, a_ctx, (unsigned char*)kv->k + l * k_layer + seq0 * k_seq,
+                                  (unsigned char*)kv->vt + l * k_layer + seq0 * k_seq, kv->k_scale + l * s_layer + seq0 * s_seq,
+                                  kv->v_scale + l * s_layer + seq0 * s_seq, nseq, m->Hkv, rows_per_seq, kv->ctx, HD, st));
     }
     CHECK(wide(ws->attn, L.o_w, L.o8, ws->q8, ws->q8s, nullptr, ws->h, ws->h, rows, Hd, m->Hq * HD, Hd, Hd,
                HWOCR_EPI_RESIDUAL, st));
@@ -335,10 +335,10 @@ static int decode_attention(const hwocr_decoder* m, const hwocr_dec_ws* ws, cons
   const float scale = 1.0f / sqrtf((float)HD);
   if (kv->fp8) {
     const long s_layer = (long)kv->nseq_max * m->Hkv * kv->ctx;
-    return hwocr_attn_decode_qkv_fp8kv(slabs, nslab, (long)nseq * QW, bias, (unsigned char*)kv->k + l * k_layer, (unsigned char*)kv->vt + l * k_layer,
-                                       kv->k_scale + l * s_layer, kv->v_scale + l * s_layer, gs->lens, gs->rope_delta, m->rope_cos, m->rope_sin,
-                                       ws->attn, ws->part_o, ws->part_ml, arrive, nseq, m->Hq, m->Hkv, attn_splits, scale, kv->ctx, m->max_pos,
-                                       gs->status, st);
+    return hwocr_attn_decode_qkv_fp8kv_hd(slabs, nslab, (long)nseq * QW, bias, (unsigned char*)kv->k + l * k_layer,
+                                          (unsigned char*)kv->vt + l * k_layer, kv->k_scale + l * s_layer, kv->v_scale + l * s_layer, gs->lens,
+                                          gs->rope_delta, m->rope_cos, m->rope_sin, ws->attn, ws->part_o, ws->part_ml, arrive, nseq, m->Hq, m->Hkv,
+                                          attn_splits, scale, kv->ctx, m->max_pos, HD, gs->status, st);
   }
   return hwocr_attn_decode_qkv(slabs, nslab, (long)nseq * QW, bias, B(kv->k) + l * k_layer, B(kv->vt) + l * k_layer, gs->lens, gs->rope_delta,
                                m->rope_cos, m->rope_sin, ws->attn, ws->part_o, ws->part_ml, arrive, nseq, m->Hq, m->Hkv, attn_splits, k_seq,
@@ -416,7 +416,7 @@ extern "C" int hwocr_decode_step(const hwocr_decoder* m, const hwocr_dec_ws* ws,
   if (!m || !ws || !kv || !gs || nseq <= 0 || nseq > 256 || nseq > kv->nseq_max || attn_splits < 1 || attn_splits > 16 ||
       m->max_pos < 1 || (m->head_dim != 128 && m->head_dim != 256) || (m->head_dim != 128 && kv->tiled))
     return HWOCR_EINVAL;
-  if (kv->fp8 && (m->head_dim != 256 || kv->tiled || !kv->k_scale || !kv->v_scale || (kv->ctx % 32))) return HWOCR_EINVAL;
+  if (kv->fp8 && (kv->tiled || !kv->k_scale || !kv->v_scale || (kv->ctx % 32))) return HWOCR_EINVAL;
   const int HD = m->head_dim, G = m->gemma;
   const int Hd = m->hidden, QW = (m->Hq + 2 * m->Hkv) * HD, OW = m->Hq * HD;
   const long k_head = (long)kv->ctx * HD, k_seq = (long)m->Hkv * k_head, k_layer = (long)kv->nseq_max * k_seq;

@@ -406,19 +406,20 @@ def decode_slab_floats(cfg: ModelConfig, reads: int, fp8: bool = False) -> int:
     return n
 
 
-def decode_plan(cfg: ModelConfig, reads: int, fp8: bool = False, attn_splits: int = 0) -> dict:
+def decode_plan(cfg: ModelConfig, reads: int, fp8: bool = False, attn_splits: int = 0, fp8_kv: bool | None = None) -> dict:
     """Kernel instances one decode step of `cfg` runs at `reads` reads in flight, as hwocr_decode_step itself lists them under plan
     recording (hwocr_plan_begin; one decoder layer + the LM head + the token selection; nothing is launched): {gemm name: (N, K, epi,
     splitk, variant)} for the five GEMMs, "attn": the attention instance, "launches": every line.  fp8: the engine was built with
-    E4M3 decode weights (fp8 + fp8_decode).  Host-only."""
+    E4M3 decode weights (fp8 + fp8_decode); fp8_kv: as ReadEngine (None: the default of an engine with these fp8 weights and no
+    environment switch).  Host-only."""
     import re
 
     lib = _lib.hip()
     dec, one, _keep = _placeholder_decoder(cfg, fp8)
     ws = _lib.DecWs(**{k: one for k in ("h", "hn", "qkv", "q", "attn", "act", "slabs", "part_o", "part_ml", "arrive", "select_ws", "logits")})
     kv = _lib.Kv(k=one, vt=one, nseq_max=max(reads, 1), ctx=2048, tiled=1 if cfg.head_dim == 128 else 0)
-    if fp8 and cfg.head_dim == 256:   # the fp8 engine of a 256-wide-head model keeps an E4M3 KV cache (ReadEngine.fp8_kv)
-        kv.k_scale, kv.v_scale, kv.fp8 = one, one, 1
+    if kv_cache_e4m3(fp8_kv, fp8, cfg.head_dim, env={}):   # the E4M3 KV cache (ReadEngine.fp8_kv)
+        kv.k_scale, kv.v_scale, kv.fp8, kv.tiled = one, one, 1, 0
     eos = (C.c_int * 4)(0, 0, 0, 0)
     gs = _lib.GenState(cur_ids=one, lens=one, n_gen=one, finished=one, out_tokens=one, rope_delta=one, max_new=8, min_new=0, n_eos=1,
                        pad_id=0, eos=eos, seen=None, seen_ld=0, rep_penalty=1.0, status=one, do_sample=0, temperature=1.0, top_k=0,
@@ -447,7 +448,8 @@ def decode_plan(cfg: ModelConfig, reads: int, fp8: bool = False, attn_splits: in
     return out
 
 
-def wide_plan(cfg: ModelConfig, hw: tuple[int, int], pages: int, reads: int, prompt_len: int, fp8: bool = False) -> list[str]:
+def wide_plan(cfg: ModelConfig, hw: tuple[int, int], pages: int, reads: int, prompt_len: int, fp8: bool = False,
+              fp8_kv: bool | None = None) -> list[str]:
     """The launches of ONE hwocr_vit_forward over `pages` pages of hw = (H, W) pixels followed by ONE hwocr_prefill of `reads`
     prompts of `prompt_len` tokens, as the library itself lists them under plan recording (hwocr_plan_begin: every launcher checks
     its arguments, notes kernel instance + geometry and returns without touching the device) — so this is the launch sequence of
@@ -504,8 +506,8 @@ def wide_plan(cfg: ModelConfig, hw: tuple[int, int], pages: int, reads: int, pro
         dws.q8, dws.q8s = one, one
     Tp = _ceil(prompt_len, 64)
     kv = _lib.Kv(k=one, vt=one, nseq_max=max(reads, 1), ctx=_ceil(Tp + 64, 64), tiled=1 if HD == 128 else 0)
-    if fp8 and HD == 256:   # the E4M3 KV cache of the fp8 engine (ReadEngine.fp8_kv): the prefill fills it from a bf16 scratch
-        kv.k_scale, kv.v_scale, kv.fp8 = one, one, 1
+    if kv_cache_e4m3(fp8_kv, fp8, HD, env={}):   # the E4M3 KV cache (ReadEngine.fp8_kv): the prefill fills it from a bf16 scratch
+        kv.k_scale, kv.v_scale, kv.fp8, kv.tiled = one, one, 1, 0
         dws.kt, dws.vtt = one, one
     eos = (C.c_int * 4)(0, 0, 0, 0)
     gs = _lib.GenState(cur_ids=one, lens=one, n_gen=one, finished=one, out_tokens=one, rope_delta=one, max_new=8, min_new=0,
@@ -562,6 +564,26 @@ class ReadSource:
             return list(range(lo, self._next))
 
 
+def kv_cache_e4m3(fp8_kv: bool | None, fp8: bool, head_dim: int, env=None) -> bool:
+    """Whether a ReadEngine keeps an E4M3 KV cache (hwocr_kv.fp8) rather than bf16; host-only, no device.
+      fp8_kv True / False: E4M3 / bf16, for head_dim 128 or 256, with or without fp8 weights.
+      fp8_kv None: HWOCR_KV_DTYPE=e4m3 / bf16 in the environment decides for every model; unset, the fp8 engine of a 256-wide-head
+      model (PaliGemma) keeps an E4M3 cache unless HWOCR_FP8_KV=0, every other engine a bf16 one."""
+    env = os.environ if env is None else env
+    if head_dim not in (128, 256):
+        raise ValueError(f"head_dim {head_dim}: the KV cache is defined for 128- and 256-wide heads")
+    if fp8_kv is not None:
+        return bool(fp8_kv)
+    kind = env.get("HWOCR_KV_DTYPE", "").strip().lower()
+    if kind == "e4m3":
+        return True
+    if kind == "bf16":
+        return False
+    if kind:
+        raise ValueError(f"HWOCR_KV_DTYPE={kind!r}: expected 'e4m3' or 'bf16'")
+    return bool(fp8) and head_dim == 256 and env.get("HWOCR_FP8_KV", "1") not in ("", "0")
+
+
 class ReadEngine:
     VIT_MAX_GRID = 2048  # rows of the vision rotary table: the longest page side in patches (smart_resize admits 200:1 strips:
     #                      sqrt(1024^2 * 200) / 14 = 1035 patches at the reference's max_pixels); encode_pages checks it
@@ -575,7 +597,9 @@ class ReadEngine:
         of 128) on E4M3 copies of the weights with per-token activation scales (BASELINE config 4); norms and attention stay
         bf16.  fp8_decode (with fp8; default: HWOCR_FP8_DECODE, off): the decode GEMMs and the LM head also read E4M3 weight codes
         (hwocr_gemm_skinny_w8: half the weight bytes per step).  Exact, but measured SLOWER than the bf16 decode weights on this
-        part (PaliGemma-3B, 252 reads: 6.08 vs 5.86 ms per token — the decode GEMMs are not weight-byte bound), hence opt-in."""
+        part (PaliGemma-3B, 252 reads: 6.08 vs 5.86 ms per token — the decode GEMMs are not weight-byte bound), hence opt-in.
+        fp8_kv: E4M3 KV cache (True) or bf16 (False) for 128- or 256-wide heads, independent of fp8; None: HWOCR_KV_DTYPE=e4m3 / bf16,
+        else E4M3 only for the fp8 engine of a 256-wide-head model (unless HWOCR_FP8_KV=0) - kv_cache_e4m3."""
         cfg.validate()
         if not torch.cuda.is_available():
             raise _lib.HwocrError("ReadEngine needs an MI355X (ROCm) device: there is no CPU path")
@@ -593,9 +617,9 @@ class ReadEngine:
         self.prefill_batch = prefill_batch
         self.attn_splits = attn_splits or int(os.environ.get("HWOCR_ATTN_SPLITS", "0"))  # 0: pick_attn_splits
         self.fp8 = bool(fp8)
-        # E4M3 KV cache (with fp8, 256-wide heads = PaliGemma / Gemma; default on, HWOCR_FP8_KV=0 or fp8_kv=False: bf16 cache): one byte
-        # per cached element + one scale per token and kv head; the decode attention of config 4 streams half the bytes
-        self.fp8_kv = self.fp8 and cfg.head_dim == 256 and (os.environ.get("HWOCR_FP8_KV", "1") not in ("", "0") if fp8_kv is None else bool(fp8_kv))
+        # E4M3 KV cache: one byte per cached element + one scale per token and kv head, the decode attention streams half the bytes
+        # (kv_cache_e4m3: which requests and which defaults give it)
+        self.fp8_kv = kv_cache_e4m3(fp8_kv, self.fp8, cfg.head_dim)
         self.fp8_decode = self.fp8 and (os.environ.get("HWOCR_FP8_DECODE", "0") not in ("", "0") if fp8_decode is None else bool(fp8_decode))
         self.collect_timings = False
         self.timings = {}
