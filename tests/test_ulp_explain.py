@@ -56,3 +56,28 @@ def test_gated_candidates_cover_a_gate_and_an_up_flip():
     u_up = bf16_neighbours(rbf(u_pre))[:, 2]
     v = rbf(torch.nn.functional.silu(g_dn)) * u_up
     assert bool(((c - v.unsqueeze(1)).abs() < 1e-7).any(dim=1).all())
+
+
+def test_a_small_output_keeps_the_hard_bound_even_for_one_explained_outlier():
+    """Below 1 / max_frac elements the count floor is 0: one element beyond the hard bound fails even when it is exactly one rounding
+    flip away from the reference (the floor used to be 2 whatever the size)."""
+    g = torch.Generator().manual_seed(5)
+    v = torch.randn(4096, generator=g) * 2.0
+    want = _epilogue_ref(v.view(1, -1), torch.zeros(4096), None, 6).flatten()
+    out = want.to(torch.bfloat16)
+    cands = lambda idx: _activation_candidates(v[idx], 6)  # noqa: E731
+    assert assert_close_bf16_explained(out.view(1, -1), want.view(1, -1), ulps=0.51, atol=0.0, what="clean", mag=None,
+                                       candidates=cands) == 0
+    # element 7 with x = bf16(acc + bias) one ulp up: explained, and at 4096 outputs no longer tolerated
+    x_up = bf16_neighbours(rbf(v[7:8]))[:, 2]
+    out[7] = _epilogue_ref(x_up.view(1, 1), torch.zeros(1), None, 6).flatten().to(torch.bfloat16)[0]
+    assert float((out[7].float() - want[7]).abs()) > 0
+    with pytest.raises(AssertionError, match="not rare coincidences"):
+        assert_close_bf16_explained(out.view(1, -1), want.view(1, -1), ulps=0.51, atol=0.0, what="one", mag=None, candidates=cands)
+    # the same single outlier among 250 000 outputs (4e-6 x 250 000 = 1) is tolerated
+    big_want = want.repeat(62)[:250000].clone()
+    big_out = big_want.to(torch.bfloat16)
+    big_out[7] = out[7]
+    big_v = v.repeat(62)[:250000]
+    assert assert_close_bf16_explained(big_out.view(1, -1), big_want.view(1, -1), ulps=0.51, atol=0.0, what="one of many", mag=None,
+                                       candidates=lambda idx: _activation_candidates(big_v[idx], 6)) == 1
