@@ -19,6 +19,8 @@ from dataclasses import dataclass
 import torch
 import torch.nn.functional as F
 
+from oracle.qwen2vl_ref import attend, kv_round_trip
+
 
 @dataclass
 class PaliRefConfig:
@@ -60,9 +62,11 @@ def rotate_half(x: torch.Tensor) -> torch.Tensor:
 class PaliGemmaRef:
     """Functional restatement over a state dict with HF 5.x parameter names (model.vision_tower.*, model.language_model.*)."""
 
-    def __init__(self, cfg: PaliRefConfig, sd: dict):
+    def __init__(self, cfg: PaliRefConfig, sd: dict, kv_quant: bool = False):
+        """kv_quant: the E4M3 KV cache contract, as oracle/qwen2vl_ref.Qwen2VLRef's (off by default)."""
         self.c = cfg
         self.sd = sd
+        self.kv_quant = kv_quant
         self.dtype = sd["model.language_model.embed_tokens.weight"].dtype
         self.trace: dict = {}
 
@@ -130,16 +134,19 @@ class PaliGemmaRef:
             past = 0
             if cache[l] is not None:
                 past = cache[l][0].shape[1]
+                if self.kv_quant:   # the appended rows are quantised before they are attended over
+                    k, v = kv_round_trip(k), kv_round_trip(v)
                 k = torch.cat([cache[l][0], k], dim=1)
                 v = torch.cat([cache[l][1], v], dim=1)
-            cache[l] = (k, v)
+                cache[l] = (k, v)
+            else:   # the prefix attends over bf16 K / V; the cache keeps the quantised rows
+                cache[l] = (kv_round_trip(k), kv_round_trip(v)) if self.kv_quant else (k, v)
             g = c.q_heads // c.kv_heads
             kk, vv = k.repeat_interleave(g, dim=0), v.repeat_interleave(g, dim=0)
             mask = None
             if T > 1 and not bidirectional:
                 mask = torch.ones(T, past + T, dtype=torch.bool).tril(past)
-            a = F.scaled_dot_product_attention(q.unsqueeze(0), kk.unsqueeze(0), vv.unsqueeze(0), attn_mask=mask,
-                                               scale=hd ** -0.5).squeeze(0)
+            a = attend(q, kk, vv, mask, hd ** -0.5)
             h = h + F.linear(a.transpose(0, 1).reshape(T, c.q_heads * hd), self.w(p + "self_attn.o_proj.weight"))
             x = gemma_rms_norm(h, self.w(p + "post_attention_layernorm.weight"), c.eps)
             gate = F.gelu(F.linear(x, self.w(p + "mlp.gate_proj.weight")), approximate="tanh")

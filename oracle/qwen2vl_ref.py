@@ -21,6 +21,8 @@ from dataclasses import dataclass, field
 import torch
 import torch.nn.functional as F
 
+from oracle import fp8_ref
+
 
 @dataclass
 class RefConfig:
@@ -150,12 +152,33 @@ def rope_index(input_ids: torch.Tensor, image_token_id: int, grids: list[tuple[i
     return pos, int(pos.max()) + 1 - T
 
 
-class Qwen2VLRef:
-    """Functional restatement over a state dict with HF parameter names (model.visual.*, model.language_model.*)."""
+def kv_round_trip(x: torch.Tensor) -> torch.Tensor:
+    """The E4M3 KV cache's view of cached rows (hwocr_kv.fp8): every (kv head, token) row of head_dim -> its
+    fp8_ref.quant_rows codes times the row's scale, exact in fp32.  x [kvh, T, hd] (bf16) -> fp32 of the same shape."""
+    q, s = fp8_ref.quant_rows(x.reshape(-1, x.shape[-1]))
+    return (q.float() * s[:, None]).reshape(x.shape)
 
-    def __init__(self, cfg: RefConfig, sd: dict):
+
+def attend(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mask, scale: float) -> torch.Tensor:
+    """scaled_dot_product_attention of [heads, T, hd] operands.  Over an E4M3 cache (fp32 k / v: kv_round_trip) the scores, softmax
+    and weighted sum run in fp32 over the dequantised rows and the output is rounded once to q's dtype, as the decode kernel does."""
+    if k.dtype == q.dtype:
+        return F.scaled_dot_product_attention(q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), attn_mask=mask, scale=scale).squeeze(0)
+    return F.scaled_dot_product_attention(q.float().unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0), attn_mask=mask,
+                                          scale=scale).squeeze(0).to(q.dtype)
+
+
+class Qwen2VLRef:
+    """Functional restatement over a state dict with HF parameter names (model.visual.*, model.language_model.*).
+
+    kv_quant (off by default; HF has no counterpart): the E4M3 KV cache contract of DESIGN.md / hwocr.h.  The prompt attends over
+    its bf16 K / V, after which every cached (kv head, token) row is replaced by its quant_rows round trip (kv_round_trip); a decode
+    step quantises the row it appends BEFORE it attends over it, and attends in fp32 (attend)."""
+
+    def __init__(self, cfg: RefConfig, sd: dict, kv_quant: bool = False):
         self.c = cfg
         self.sd = sd
+        self.kv_quant = kv_quant
         self.dtype = sd["model.language_model.embed_tokens.weight"].dtype
         self.trace: dict = {}
 
@@ -313,17 +336,20 @@ class Qwen2VLRef:
             if cache is not None:
                 if cache[l] is not None:
                     past = cache[l][0].shape[1]
+                    if self.kv_quant:   # the appended rows are quantised before they are attended over
+                        k, v = kv_round_trip(k), kv_round_trip(v)
                     k = torch.cat([cache[l][0], k], dim=1)
                     v = torch.cat([cache[l][1], v], dim=1)
-                cache[l] = (k, v)
+                    cache[l] = (k, v)
+                else:   # the prompt attends over bf16 K / V; the cache keeps the quantised rows
+                    cache[l] = (kv_round_trip(k), kv_round_trip(v)) if self.kv_quant else (k, v)
             g = c.q_heads // c.kv_heads
             kk = k.repeat_interleave(g, dim=0)
             vv = v.repeat_interleave(g, dim=0)
             mask = None
             if T > 1:
                 mask = torch.ones(T, past + T, dtype=torch.bool).tril(past)
-            a = F.scaled_dot_product_attention(q.unsqueeze(0), kk.unsqueeze(0), vv.unsqueeze(0), attn_mask=mask,
-                                               scale=hd ** -0.5).squeeze(0)
+            a = attend(q, kk, vv, mask, hd ** -0.5)
             a = a.transpose(0, 1).reshape(T, c.q_heads * hd)
             h = h + F.linear(a, self.w(p + "self_attn.o_proj.weight"))
             x = rms_norm(h, self.w(p + "post_attention_layernorm.weight"), c.eps)

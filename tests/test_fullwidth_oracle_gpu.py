@@ -16,22 +16,11 @@ import torch
 import torch.nn.functional as F
 from PIL import Image
 
+from tests._parity import check_logits as _check_logits
+
 pytestmark = pytest.mark.gpu
 
 N_NEW = 6
-
-
-def _check_logits(got, want, toks_engine, toks_oracle, what):
-    got, want = got.float().cpu(), want.float()
-    scale = max(1.0, float(want.abs().max()))
-    d = (got - want).abs()
-    assert float(d.mean()) <= 5e-3 * scale, f"{what}: mean logit error {float(d.mean())} (scale {scale})"
-    assert float(d.flatten().quantile(0.999)) <= 3e-2 * scale, f"{what}: p99.9 {float(d.flatten().quantile(0.999))} (scale {scale})"
-    assert float(d.max()) <= 6e-2 * scale, f"{what}: teacher-forced logits differ by {float(d.max())} (scale {scale})"
-    top2 = want.topk(2, -1).values
-    decisive = (top2[:, 0] - top2[:, 1]) > 0.05
-    agree = torch.tensor([a == b for a, b in zip(toks_engine, toks_oracle)])
-    assert bool(agree[decisive].all()), (what, toks_engine, toks_oracle)
 
 
 def _check_embeddings(eng, page, want, what):
