@@ -9,21 +9,26 @@ token ids -> merged text):
     -> vision tower -> prefill -> N_out greedy tokens per read (min_new == max_new, so the work is fixed: random-init
        logits otherwise hit EOS at once) -> gather token streams to rank 0 -> per page compare_versions(read 1, read 2)
        + merge_versions(all reads).
-Beside `value` the JSON carries the same step with the PCIe upload of the raw pages inside the clock
-(`with_upload`) and with the reference's default host (PIL) preprocessing instead of the device path
-(`host_preprocess_path`), plus the single-page latency of BASELINE config 2 as literally stated (one page, 3 reads).
 Weights: random init at the Qwen2-VL-2B shape (no checkpoint is reachable offline).
 
     python bench.py --gpus N --steps K --warmup W      N > 1 without WORLD_SIZE: this process only spawns N ranks (one per
                                                        GPU, RCCL) and relays rank 0's line; it never touches the GPU itself
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     (ranks made by the launcher)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+A plain run does what the headline needs and no more: set up, warm up, time K steps, write --dump-outputs, print ONE JSON line
+on rank 0 (contract in the task statement).  Beside `value` that line carries what the timed region's own events give:
     roofline      dominant kernel = gemm_wide (bf16 MFMA): algorithmic FLOPs / HIP-event time of its launches inside
-                  the first timed steps, against the 2.5 PFLOP/s dense bf16 peak
+                  the timed steps, against the 2.5 PFLOP/s dense bf16 peak
+    phases_ms_per_step, decode_roofline   the lanes' phase times in the timed steps
+--full adds every leg that takes runs of its own (over a minute more; --no-extras / --no-cpu-baseline leave parts of it out):
+    with_upload, host_preprocess_path, single_page   the same step with the PCIe upload of the raw pages inside the clock, with
+                  the reference's default host (PIL) preprocessing instead of the device path, and the single-page latency of
+                  BASELINE config 2 as literally stated (one page, 3 reads)
+    one_batch_at_a_time   (lanes > 1) one batch at a time; `roofline` is then taken from it: the kernel alone on the chip
     cpu_baseline  the CPU oracle (oracle/, a restatement of the HF arithmetic the reference runs) timed on this host: one whole
                   read at full depth on the engine's own weights, 32 decode steps measured and the rest scaled per token
                   (see `sample`); parity_full_depth_vs_oracle = the engine held to that very read, teacher-forced
+    parity_vs_hf_goldens  the tiny HF goldens and the trained checkpoints of tests/golden read through the engine
 """
 from __future__ import annotations
 
@@ -531,8 +536,12 @@ def main() -> None:
     ap.add_argument("--model", default="qwen2-vl-2b")
     ap.add_argument("--vit-batch", type=int, default=12)
     ap.add_argument("--prefill-batch", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the with_upload / host_preprocess_path / single-page legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline: with_upload, one_batch_at_a_time, "
+                         "host_preprocess_path, single_page, cpu_baseline, parity_full_depth_vs_oracle, parity_vs_hf_goldens")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the parity legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the with_upload / one_batch_at_a_time / host_preprocess_path / single-page legs")
     ap.add_argument("--profile-steps", type=int, default=0, help="(ignored: every wide-GEMM launch of the timed region carries HIP events)")
     ap.add_argument("--lanes", type=int, default=2,
                     help="batches in flight on the GPU, one engine lane, host thread and HIP stream each (pipeline.LanePipeline); "
@@ -547,6 +556,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    extras_on = args.full and not args.no_extras          # the legs that take runs of their own beside the timed steps
+    cpu_on = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -576,7 +587,7 @@ def main() -> None:
     ctx = 2048 if n_img_tokens + 64 + args.new_tokens <= 2048 else (n_img_tokens + 128 + args.new_tokens + 63) // 64 * 64
     eng = engine.ReadEngine(cfg, sd, max_reads=n_reads, ctx=ctx, device=str(dev), vit_batch=args.vit_batch,
                             prefill_batch=args.prefill_batch, fp8=args.fp8)
-    if not (world_env == 1 and not args.no_cpu_baseline):
+    if not (world_env == 1 and cpu_on):
         del sd  # (else kept: the CPU baseline runs the oracle on a host copy of these very weights; the engine aliases them)
     eng.collect_timings = True
     tok = tokenizer.ByteTokenizer(cfg, fold_unknown=True)
@@ -697,10 +708,10 @@ def main() -> None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax)
 
-    # ---- legs outside `value` (rank 0, N = 1 only): the same step with the raw pages uploaded inside the clock, with the
+    # ---- legs outside `value` (--full; rank 0, N = 1 only): the same step with the raw pages uploaded inside the clock, with the
     # reference's default host preprocessing, and BASELINE config 2 as literally stated (one page, its 3 reads in flight)
     extras = {}
-    solo = world == 1 and not args.no_extras
+    solo = world == 1 and extras_on
     if solo:
         k_up = max(2, 2 * len(pipe.engines))
         torch.cuda.synchronize()
@@ -711,7 +722,7 @@ def main() -> None:
         extras["with_upload"] = {"value": args.pages / up_s, "unit": "pages/s", "ms_per_step": up_s * 1e3, "steps": k_up,
                                  "note": "the timed schedule with the raw pages starting in host memory (pageable): 3 MB per page over "
                                          "PCIe inside the clock"}
-    if len(pipe.engines) > 1 and not args.no_extras:
+    if len(pipe.engines) > 1 and extras_on:
         # one batch at a time on one stream (the schedule of rounds 1-2): what the overlap buys, the phase times of a batch that
         # has the chip to itself, and the dominant kernel's rate when nothing runs beside it.  Run on EVERY rank at every --gpus N
         # (the step's token gather is a collective): `roofline` then means the same thing in a BENCH line and in a SCALE line —
@@ -781,7 +792,8 @@ def main() -> None:
             "one_batch_at_a_time leg (2 steps after the timed region): the kernel alone on the chip"
         roof_steps, roof_wall = 2, extras["one_batch_at_a_time"]["ms_per_step"] * 2e-3
     else:
-        achieved, roof_ms, roof_n, roof_where = in_region["achieved"], ms.value, int(n.value), "the timed region"
+        achieved, roof_ms, roof_n, roof_where = in_region["achieved"], ms.value, int(n.value), "the timed region" + (
+            " (two lanes share the chip: --full measures the kernel alone)" if len(pipe.engines) > 1 else "")
         roof_steps, roof_wall = prof_steps, t_prof
     mean = lambda k: float(np.mean([p[k] for p in phases]))  # noqa: E731
     T = len(prompts[0])
@@ -849,14 +861,14 @@ def main() -> None:
         "phases_ms_per_step": {"preprocess": mean("preprocess_ms"), "vision": mean("vision_ms"), "prefill": mean("prefill_ms"),
                                "decode": mean("decode_ms"), "decode_per_token": dec_ms,
                                "note": ("wall time of each phase of a batch WHILE the other lane's batch shares the chip (they overlap: the "
-                                        "sum exceeds ms_per_step); one_batch_at_a_time has the phases of a batch alone"
+                                        "sum exceeds ms_per_step); one_batch_at_a_time (--full) has the phases of a batch alone"
                                         if len(pipe.engines) > 1 else "one batch at a time")},
         "decode_roofline": {"bound": "hbm", "bytes_per_step": w_bytes + kv_bytes, "achieved": (w_bytes + kv_bytes) / (dec_alone_ms * 1e-3) / 1e9,
                             "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": (w_bytes + kv_bytes) / (dec_alone_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                             "ms_per_token": dec_alone_ms, "measured": "decode of a batch alone on the chip" if alone else "timed region"},
     }
     out.update(extras)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and cpu_on:
         try:
             sd_cpu = {k: v.to("cpu") for k, v in engine.normalize_keys(sd).items()}
             del sd

@@ -38,3 +38,9 @@ def test_dump_outputs_without_a_second_read(tmp_path):
 def test_steps_must_be_positive():
     proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
     assert proc.returncode == 2 and "--steps must be >= 1" in proc.stderr
+
+
+def test_full_is_an_option_of_its_own():
+    """--full (the legs beside the headline) parses, and --steps stays bounded with it."""
+    proc = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "0"], capture_output=True, text=True)
+    assert proc.returncode == 2 and "--steps must be >= 1" in proc.stderr

@@ -6,7 +6,7 @@ TAG=$1; shift
 R=$PWD
 OUT=$R/gpurun_out
 mkdir -p $OUT
-python3 $R/bench.py --no-cpu-baseline "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python3 $R/bench.py --full --no-cpu-baseline "$@" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 echo "bench done"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_cfg
