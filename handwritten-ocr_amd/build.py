@@ -18,7 +18,7 @@ HIP_SOURCES = ["gemm.hip", "gemm256.hip", "gemm256w4.hip", "gemm_stream.hip", "g
 # attention_vit80x.hip: its score MFMAs must write arch VGPRs (the accumulator file is owned by its inline asm, see the file)
 EXTRA_FLAGS = {"attention_vit80x.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
 HIP_LIB = os.path.join(CSRC, "libhwocr_hip.so")
-DIAG_LIB = os.path.join(CSRC, "diag", "libhwocr_hip_diag.so")  # -DHWOCR_DIAG: measurement variants with WRONG results; tools/ only
+DIAG_LIB = os.path.join(CSRC, "diag", "libhwocr_hip_diag.so")  # -DHWOCR_DIAG: the A/B switches among product kernels; tools/ only
 TEXT_LIB = os.path.join(CSRC, "libhwocr_text.so")
 
 
@@ -44,12 +44,12 @@ def hipcc_path() -> str:
 
 
 def build_hip(force: bool = False, diag: bool = False) -> str:
-    """diag=True: the library with -DHWOCR_DIAG (the ablation / timeline variants of the 256x256 GEMM that tools/bench_gemm_ablate.py
-    and tools/bench_gemm_timeline.py measure; they compute WRONG results by construction) into csrc/diag/ — never what _lib.hip()
-    loads unless a tool points it there (use_diag_library)."""
+    """diag=True: the library with -DHWOCR_DIAG into csrc/diag/: the same kernels, with the A/B switches of concluded experiments
+    (csrc/common.h: HWOCR_DIAG_ENV_INT) read from the environment, each choosing among kernels the product launches for some shape —
+    never what _lib.hip() loads unless a tool points it there (use_diag_library)."""
     srcs = [os.path.join(CSRC, s) for s in HIP_SOURCES]
     deps = srcs + [os.path.join(CSRC, "gemm_common.h"), os.path.join(CSRC, "common.h"), os.path.join(CSRC, "attention_args.h"),
-                   os.path.join(CSRC, "diag_src", "gemm256w4_experiments.inc"), os.path.join(INCLUDE, "hwocr.h")]
+                   os.path.join(INCLUDE, "hwocr.h")]
     target = DIAG_LIB if diag else HIP_LIB
     if not force and _newer(target, deps):
         return target
@@ -75,8 +75,8 @@ def build_hip(force: bool = False, diag: bool = False) -> str:
 
 
 def use_diag_library() -> str:
-    """For tools/ only: build the -DHWOCR_DIAG library and make it the one _lib.hip() loads in THIS process (call before the first
-    _lib.hip())."""
+    """For tools/ only: build the -DHWOCR_DIAG library (the A/B switches among product kernels, see build_hip) and make it the one
+    _lib.hip() loads in THIS process (call before the first _lib.hip())."""
     global HIP_LIB
     HIP_LIB = build_hip(diag=True)
     return HIP_LIB

@@ -394,28 +394,9 @@ extern "C" int hwocr_gemm_wide(const void* X, const void* W, const void* bias, c
   }
   HWOCR_PLAN("gemm_wide_kernel<epi=%d> M=%d N=%d K=%d tiles=%d", epi, M, N, K, a.tilesM * a.tilesN);
   dim3 grid(a.tilesM * a.tilesN), block(256);
-  static const bool attr_done = [&] {  // thread-safe one-time setup: two lane threads reach a kernel's first launch together
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_LINEAR>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_RESIDUAL>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_QUICKGELU>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_SWIGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_GELU_TANH>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    hipFuncSetAttribute((const void*)gemm_wide_kernel<EPI_GEGLU>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS);
-    return true;
-  }();
-  (void)attr_done;
   if (prof) (void)hipEventRecord(ev0, stream);
-  switch (epi) {
-    case EPI_LINEAR: hipLaunchKernelGGL(gemm_wide_kernel<EPI_LINEAR>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_RESIDUAL: hipLaunchKernelGGL(gemm_wide_kernel<EPI_RESIDUAL>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_QUICKGELU: hipLaunchKernelGGL(gemm_wide_kernel<EPI_QUICKGELU>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_GELU: hipLaunchKernelGGL(gemm_wide_kernel<EPI_GELU>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_SWIGLU: hipLaunchKernelGGL(gemm_wide_kernel<EPI_SWIGLU>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_GELU_TANH: hipLaunchKernelGGL(gemm_wide_kernel<EPI_GELU_TANH>, grid, block, WIDE_LDS, stream, a); break;
-    case EPI_GEGLU: hipLaunchKernelGGL(gemm_wide_kernel<EPI_GEGLU>, grid, block, WIDE_LDS, stream, a); break;
-    default: return HWOCR_EINVAL;
-  }
+  if (!with_epilogue(WideEpis{}, epi, [&](auto e) { launch_big_lds<gemm_wide_kernel<decltype(e)::value>>(grid, block, WIDE_LDS, stream, a); }))
+    return HWOCR_EINVAL;
   if (prof) {
     (void)hipEventRecord(ev1, stream);
   }

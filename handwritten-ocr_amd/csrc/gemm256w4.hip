@@ -1,7 +1,7 @@
 // The 256x256x64 bf16 GEMM as FOUR waves of 128 x 128 per workgroup - one wave per SIMD with the whole 512-register file - beside the
-// eight waves of 128 x 64 of gemm256.hip.  gemm_wide256w4_kernel<EPI> is the product kernel (persistent tiles, the epilogues of
-// gemm256.hip; hwocr_gemm_wide256_w4 says for which shapes it is taken); the kernels under HWOCR_DIAG at the end are the experiment it
-// grew out of (tools/bench_gemm_w4.py: timing ablations, the 32x32x16 form, in-kernel cycle stamps).
+// eight waves of 128 x 64 of gemm256.hip.  This file holds gemm_wide256w4_kernel<EPI> (persistent tiles, the epilogues of gemm256.hip),
+// its launcher and the rule for which shapes it is taken (hwocr_gemm_wide256_w4).  The experiment kernels it grew out of are written
+// up in docs/LAB_NOTEBOOK.md and profiles/r03z_gemm_w4_experiment.txt.
 //
 // Why (a first four-wave form lost to the eight-wave kernel in round 1): the eight-wave main loop is 2566 shader
 // cycles per K tile against 2048 of matrix-pipe time at every CU count, under a clock the power budget sets
@@ -18,8 +18,6 @@
 //                + barrier (tile t + 1 has landed), then the 16 reads of tile t + 1's k-step-0 fragments.
 // LDS image, swizzle and DMA lane plan are those of gemm256.hip (rows of 128 B, 16-byte chunk p of row r at p ^ ((r >> 1) & 7)).
 #include "gemm_common.h"
-#include <cstdlib>
-#include <type_traits>
 #include <utility>
 
 using namespace gemm;
@@ -29,7 +27,6 @@ namespace {
 constexpr int BM = 256, BN = 256;
 constexpr int TILE = 256 * 128;      // 32 KiB per operand per K tile
 constexpr int STAGE = 2 * TILE;      // activation rows, then weight rows
-constexpr int LDS_BYTES = 2 * STAGE;  // 128 KiB
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
@@ -109,74 +106,6 @@ __device__ __forceinline__ void acc_mfma(int idx, bf16x8 wfrag, bf16x8 xfrag) {
     case 61: asm volatile("v_mfma_f32_16x16x32_bf16 a[244:247], %0, %1, a[244:247]" ::"v"(wfrag), "v"(xfrag) : "a244", "a245", "a246", "a247"); break;
     case 62: asm volatile("v_mfma_f32_16x16x32_bf16 a[248:251], %0, %1, a[248:251]" ::"v"(wfrag), "v"(xfrag) : "a248", "a249", "a250", "a251"); break;
     case 63: asm volatile("v_mfma_f32_16x16x32_bf16 a[252:255], %0, %1, a[252:255]" ::"v"(wfrag), "v"(xfrag) : "a252", "a253", "a254", "a255"); break;
-  }
-}
-__device__ __forceinline__ void acc_zero(int idx, float z) {
-  switch (idx) {
-    case 0: asm volatile("v_accvgpr_write_b32 a0, %0\n\tv_accvgpr_write_b32 a1, %0\n\tv_accvgpr_write_b32 a2, %0\n\tv_accvgpr_write_b32 a3, %0" ::"v"(z) : "a0", "a1", "a2", "a3"); break;
-    case 1: asm volatile("v_accvgpr_write_b32 a4, %0\n\tv_accvgpr_write_b32 a5, %0\n\tv_accvgpr_write_b32 a6, %0\n\tv_accvgpr_write_b32 a7, %0" ::"v"(z) : "a4", "a5", "a6", "a7"); break;
-    case 2: asm volatile("v_accvgpr_write_b32 a8, %0\n\tv_accvgpr_write_b32 a9, %0\n\tv_accvgpr_write_b32 a10, %0\n\tv_accvgpr_write_b32 a11, %0" ::"v"(z) : "a8", "a9", "a10", "a11"); break;
-    case 3: asm volatile("v_accvgpr_write_b32 a12, %0\n\tv_accvgpr_write_b32 a13, %0\n\tv_accvgpr_write_b32 a14, %0\n\tv_accvgpr_write_b32 a15, %0" ::"v"(z) : "a12", "a13", "a14", "a15"); break;
-    case 4: asm volatile("v_accvgpr_write_b32 a16, %0\n\tv_accvgpr_write_b32 a17, %0\n\tv_accvgpr_write_b32 a18, %0\n\tv_accvgpr_write_b32 a19, %0" ::"v"(z) : "a16", "a17", "a18", "a19"); break;
-    case 5: asm volatile("v_accvgpr_write_b32 a20, %0\n\tv_accvgpr_write_b32 a21, %0\n\tv_accvgpr_write_b32 a22, %0\n\tv_accvgpr_write_b32 a23, %0" ::"v"(z) : "a20", "a21", "a22", "a23"); break;
-    case 6: asm volatile("v_accvgpr_write_b32 a24, %0\n\tv_accvgpr_write_b32 a25, %0\n\tv_accvgpr_write_b32 a26, %0\n\tv_accvgpr_write_b32 a27, %0" ::"v"(z) : "a24", "a25", "a26", "a27"); break;
-    case 7: asm volatile("v_accvgpr_write_b32 a28, %0\n\tv_accvgpr_write_b32 a29, %0\n\tv_accvgpr_write_b32 a30, %0\n\tv_accvgpr_write_b32 a31, %0" ::"v"(z) : "a28", "a29", "a30", "a31"); break;
-    case 8: asm volatile("v_accvgpr_write_b32 a32, %0\n\tv_accvgpr_write_b32 a33, %0\n\tv_accvgpr_write_b32 a34, %0\n\tv_accvgpr_write_b32 a35, %0" ::"v"(z) : "a32", "a33", "a34", "a35"); break;
-    case 9: asm volatile("v_accvgpr_write_b32 a36, %0\n\tv_accvgpr_write_b32 a37, %0\n\tv_accvgpr_write_b32 a38, %0\n\tv_accvgpr_write_b32 a39, %0" ::"v"(z) : "a36", "a37", "a38", "a39"); break;
-    case 10: asm volatile("v_accvgpr_write_b32 a40, %0\n\tv_accvgpr_write_b32 a41, %0\n\tv_accvgpr_write_b32 a42, %0\n\tv_accvgpr_write_b32 a43, %0" ::"v"(z) : "a40", "a41", "a42", "a43"); break;
-    case 11: asm volatile("v_accvgpr_write_b32 a44, %0\n\tv_accvgpr_write_b32 a45, %0\n\tv_accvgpr_write_b32 a46, %0\n\tv_accvgpr_write_b32 a47, %0" ::"v"(z) : "a44", "a45", "a46", "a47"); break;
-    case 12: asm volatile("v_accvgpr_write_b32 a48, %0\n\tv_accvgpr_write_b32 a49, %0\n\tv_accvgpr_write_b32 a50, %0\n\tv_accvgpr_write_b32 a51, %0" ::"v"(z) : "a48", "a49", "a50", "a51"); break;
-    case 13: asm volatile("v_accvgpr_write_b32 a52, %0\n\tv_accvgpr_write_b32 a53, %0\n\tv_accvgpr_write_b32 a54, %0\n\tv_accvgpr_write_b32 a55, %0" ::"v"(z) : "a52", "a53", "a54", "a55"); break;
-    case 14: asm volatile("v_accvgpr_write_b32 a56, %0\n\tv_accvgpr_write_b32 a57, %0\n\tv_accvgpr_write_b32 a58, %0\n\tv_accvgpr_write_b32 a59, %0" ::"v"(z) : "a56", "a57", "a58", "a59"); break;
-    case 15: asm volatile("v_accvgpr_write_b32 a60, %0\n\tv_accvgpr_write_b32 a61, %0\n\tv_accvgpr_write_b32 a62, %0\n\tv_accvgpr_write_b32 a63, %0" ::"v"(z) : "a60", "a61", "a62", "a63"); break;
-    case 16: asm volatile("v_accvgpr_write_b32 a64, %0\n\tv_accvgpr_write_b32 a65, %0\n\tv_accvgpr_write_b32 a66, %0\n\tv_accvgpr_write_b32 a67, %0" ::"v"(z) : "a64", "a65", "a66", "a67"); break;
-    case 17: asm volatile("v_accvgpr_write_b32 a68, %0\n\tv_accvgpr_write_b32 a69, %0\n\tv_accvgpr_write_b32 a70, %0\n\tv_accvgpr_write_b32 a71, %0" ::"v"(z) : "a68", "a69", "a70", "a71"); break;
-    case 18: asm volatile("v_accvgpr_write_b32 a72, %0\n\tv_accvgpr_write_b32 a73, %0\n\tv_accvgpr_write_b32 a74, %0\n\tv_accvgpr_write_b32 a75, %0" ::"v"(z) : "a72", "a73", "a74", "a75"); break;
-    case 19: asm volatile("v_accvgpr_write_b32 a76, %0\n\tv_accvgpr_write_b32 a77, %0\n\tv_accvgpr_write_b32 a78, %0\n\tv_accvgpr_write_b32 a79, %0" ::"v"(z) : "a76", "a77", "a78", "a79"); break;
-    case 20: asm volatile("v_accvgpr_write_b32 a80, %0\n\tv_accvgpr_write_b32 a81, %0\n\tv_accvgpr_write_b32 a82, %0\n\tv_accvgpr_write_b32 a83, %0" ::"v"(z) : "a80", "a81", "a82", "a83"); break;
-    case 21: asm volatile("v_accvgpr_write_b32 a84, %0\n\tv_accvgpr_write_b32 a85, %0\n\tv_accvgpr_write_b32 a86, %0\n\tv_accvgpr_write_b32 a87, %0" ::"v"(z) : "a84", "a85", "a86", "a87"); break;
-    case 22: asm volatile("v_accvgpr_write_b32 a88, %0\n\tv_accvgpr_write_b32 a89, %0\n\tv_accvgpr_write_b32 a90, %0\n\tv_accvgpr_write_b32 a91, %0" ::"v"(z) : "a88", "a89", "a90", "a91"); break;
-    case 23: asm volatile("v_accvgpr_write_b32 a92, %0\n\tv_accvgpr_write_b32 a93, %0\n\tv_accvgpr_write_b32 a94, %0\n\tv_accvgpr_write_b32 a95, %0" ::"v"(z) : "a92", "a93", "a94", "a95"); break;
-    case 24: asm volatile("v_accvgpr_write_b32 a96, %0\n\tv_accvgpr_write_b32 a97, %0\n\tv_accvgpr_write_b32 a98, %0\n\tv_accvgpr_write_b32 a99, %0" ::"v"(z) : "a96", "a97", "a98", "a99"); break;
-    case 25: asm volatile("v_accvgpr_write_b32 a100, %0\n\tv_accvgpr_write_b32 a101, %0\n\tv_accvgpr_write_b32 a102, %0\n\tv_accvgpr_write_b32 a103, %0" ::"v"(z) : "a100", "a101", "a102", "a103"); break;
-    case 26: asm volatile("v_accvgpr_write_b32 a104, %0\n\tv_accvgpr_write_b32 a105, %0\n\tv_accvgpr_write_b32 a106, %0\n\tv_accvgpr_write_b32 a107, %0" ::"v"(z) : "a104", "a105", "a106", "a107"); break;
-    case 27: asm volatile("v_accvgpr_write_b32 a108, %0\n\tv_accvgpr_write_b32 a109, %0\n\tv_accvgpr_write_b32 a110, %0\n\tv_accvgpr_write_b32 a111, %0" ::"v"(z) : "a108", "a109", "a110", "a111"); break;
-    case 28: asm volatile("v_accvgpr_write_b32 a112, %0\n\tv_accvgpr_write_b32 a113, %0\n\tv_accvgpr_write_b32 a114, %0\n\tv_accvgpr_write_b32 a115, %0" ::"v"(z) : "a112", "a113", "a114", "a115"); break;
-    case 29: asm volatile("v_accvgpr_write_b32 a116, %0\n\tv_accvgpr_write_b32 a117, %0\n\tv_accvgpr_write_b32 a118, %0\n\tv_accvgpr_write_b32 a119, %0" ::"v"(z) : "a116", "a117", "a118", "a119"); break;
-    case 30: asm volatile("v_accvgpr_write_b32 a120, %0\n\tv_accvgpr_write_b32 a121, %0\n\tv_accvgpr_write_b32 a122, %0\n\tv_accvgpr_write_b32 a123, %0" ::"v"(z) : "a120", "a121", "a122", "a123"); break;
-    case 31: asm volatile("v_accvgpr_write_b32 a124, %0\n\tv_accvgpr_write_b32 a125, %0\n\tv_accvgpr_write_b32 a126, %0\n\tv_accvgpr_write_b32 a127, %0" ::"v"(z) : "a124", "a125", "a126", "a127"); break;
-    case 32: asm volatile("v_accvgpr_write_b32 a128, %0\n\tv_accvgpr_write_b32 a129, %0\n\tv_accvgpr_write_b32 a130, %0\n\tv_accvgpr_write_b32 a131, %0" ::"v"(z) : "a128", "a129", "a130", "a131"); break;
-    case 33: asm volatile("v_accvgpr_write_b32 a132, %0\n\tv_accvgpr_write_b32 a133, %0\n\tv_accvgpr_write_b32 a134, %0\n\tv_accvgpr_write_b32 a135, %0" ::"v"(z) : "a132", "a133", "a134", "a135"); break;
-    case 34: asm volatile("v_accvgpr_write_b32 a136, %0\n\tv_accvgpr_write_b32 a137, %0\n\tv_accvgpr_write_b32 a138, %0\n\tv_accvgpr_write_b32 a139, %0" ::"v"(z) : "a136", "a137", "a138", "a139"); break;
-    case 35: asm volatile("v_accvgpr_write_b32 a140, %0\n\tv_accvgpr_write_b32 a141, %0\n\tv_accvgpr_write_b32 a142, %0\n\tv_accvgpr_write_b32 a143, %0" ::"v"(z) : "a140", "a141", "a142", "a143"); break;
-    case 36: asm volatile("v_accvgpr_write_b32 a144, %0\n\tv_accvgpr_write_b32 a145, %0\n\tv_accvgpr_write_b32 a146, %0\n\tv_accvgpr_write_b32 a147, %0" ::"v"(z) : "a144", "a145", "a146", "a147"); break;
-    case 37: asm volatile("v_accvgpr_write_b32 a148, %0\n\tv_accvgpr_write_b32 a149, %0\n\tv_accvgpr_write_b32 a150, %0\n\tv_accvgpr_write_b32 a151, %0" ::"v"(z) : "a148", "a149", "a150", "a151"); break;
-    case 38: asm volatile("v_accvgpr_write_b32 a152, %0\n\tv_accvgpr_write_b32 a153, %0\n\tv_accvgpr_write_b32 a154, %0\n\tv_accvgpr_write_b32 a155, %0" ::"v"(z) : "a152", "a153", "a154", "a155"); break;
-    case 39: asm volatile("v_accvgpr_write_b32 a156, %0\n\tv_accvgpr_write_b32 a157, %0\n\tv_accvgpr_write_b32 a158, %0\n\tv_accvgpr_write_b32 a159, %0" ::"v"(z) : "a156", "a157", "a158", "a159"); break;
-    case 40: asm volatile("v_accvgpr_write_b32 a160, %0\n\tv_accvgpr_write_b32 a161, %0\n\tv_accvgpr_write_b32 a162, %0\n\tv_accvgpr_write_b32 a163, %0" ::"v"(z) : "a160", "a161", "a162", "a163"); break;
-    case 41: asm volatile("v_accvgpr_write_b32 a164, %0\n\tv_accvgpr_write_b32 a165, %0\n\tv_accvgpr_write_b32 a166, %0\n\tv_accvgpr_write_b32 a167, %0" ::"v"(z) : "a164", "a165", "a166", "a167"); break;
-    case 42: asm volatile("v_accvgpr_write_b32 a168, %0\n\tv_accvgpr_write_b32 a169, %0\n\tv_accvgpr_write_b32 a170, %0\n\tv_accvgpr_write_b32 a171, %0" ::"v"(z) : "a168", "a169", "a170", "a171"); break;
-    case 43: asm volatile("v_accvgpr_write_b32 a172, %0\n\tv_accvgpr_write_b32 a173, %0\n\tv_accvgpr_write_b32 a174, %0\n\tv_accvgpr_write_b32 a175, %0" ::"v"(z) : "a172", "a173", "a174", "a175"); break;
-    case 44: asm volatile("v_accvgpr_write_b32 a176, %0\n\tv_accvgpr_write_b32 a177, %0\n\tv_accvgpr_write_b32 a178, %0\n\tv_accvgpr_write_b32 a179, %0" ::"v"(z) : "a176", "a177", "a178", "a179"); break;
-    case 45: asm volatile("v_accvgpr_write_b32 a180, %0\n\tv_accvgpr_write_b32 a181, %0\n\tv_accvgpr_write_b32 a182, %0\n\tv_accvgpr_write_b32 a183, %0" ::"v"(z) : "a180", "a181", "a182", "a183"); break;
-    case 46: asm volatile("v_accvgpr_write_b32 a184, %0\n\tv_accvgpr_write_b32 a185, %0\n\tv_accvgpr_write_b32 a186, %0\n\tv_accvgpr_write_b32 a187, %0" ::"v"(z) : "a184", "a185", "a186", "a187"); break;
-    case 47: asm volatile("v_accvgpr_write_b32 a188, %0\n\tv_accvgpr_write_b32 a189, %0\n\tv_accvgpr_write_b32 a190, %0\n\tv_accvgpr_write_b32 a191, %0" ::"v"(z) : "a188", "a189", "a190", "a191"); break;
-    case 48: asm volatile("v_accvgpr_write_b32 a192, %0\n\tv_accvgpr_write_b32 a193, %0\n\tv_accvgpr_write_b32 a194, %0\n\tv_accvgpr_write_b32 a195, %0" ::"v"(z) : "a192", "a193", "a194", "a195"); break;
-    case 49: asm volatile("v_accvgpr_write_b32 a196, %0\n\tv_accvgpr_write_b32 a197, %0\n\tv_accvgpr_write_b32 a198, %0\n\tv_accvgpr_write_b32 a199, %0" ::"v"(z) : "a196", "a197", "a198", "a199"); break;
-    case 50: asm volatile("v_accvgpr_write_b32 a200, %0\n\tv_accvgpr_write_b32 a201, %0\n\tv_accvgpr_write_b32 a202, %0\n\tv_accvgpr_write_b32 a203, %0" ::"v"(z) : "a200", "a201", "a202", "a203"); break;
-    case 51: asm volatile("v_accvgpr_write_b32 a204, %0\n\tv_accvgpr_write_b32 a205, %0\n\tv_accvgpr_write_b32 a206, %0\n\tv_accvgpr_write_b32 a207, %0" ::"v"(z) : "a204", "a205", "a206", "a207"); break;
-    case 52: asm volatile("v_accvgpr_write_b32 a208, %0\n\tv_accvgpr_write_b32 a209, %0\n\tv_accvgpr_write_b32 a210, %0\n\tv_accvgpr_write_b32 a211, %0" ::"v"(z) : "a208", "a209", "a210", "a211"); break;
-    case 53: asm volatile("v_accvgpr_write_b32 a212, %0\n\tv_accvgpr_write_b32 a213, %0\n\tv_accvgpr_write_b32 a214, %0\n\tv_accvgpr_write_b32 a215, %0" ::"v"(z) : "a212", "a213", "a214", "a215"); break;
-    case 54: asm volatile("v_accvgpr_write_b32 a216, %0\n\tv_accvgpr_write_b32 a217, %0\n\tv_accvgpr_write_b32 a218, %0\n\tv_accvgpr_write_b32 a219, %0" ::"v"(z) : "a216", "a217", "a218", "a219"); break;
-    case 55: asm volatile("v_accvgpr_write_b32 a220, %0\n\tv_accvgpr_write_b32 a221, %0\n\tv_accvgpr_write_b32 a222, %0\n\tv_accvgpr_write_b32 a223, %0" ::"v"(z) : "a220", "a221", "a222", "a223"); break;
-    case 56: asm volatile("v_accvgpr_write_b32 a224, %0\n\tv_accvgpr_write_b32 a225, %0\n\tv_accvgpr_write_b32 a226, %0\n\tv_accvgpr_write_b32 a227, %0" ::"v"(z) : "a224", "a225", "a226", "a227"); break;
-    case 57: asm volatile("v_accvgpr_write_b32 a228, %0\n\tv_accvgpr_write_b32 a229, %0\n\tv_accvgpr_write_b32 a230, %0\n\tv_accvgpr_write_b32 a231, %0" ::"v"(z) : "a228", "a229", "a230", "a231"); break;
-    case 58: asm volatile("v_accvgpr_write_b32 a232, %0\n\tv_accvgpr_write_b32 a233, %0\n\tv_accvgpr_write_b32 a234, %0\n\tv_accvgpr_write_b32 a235, %0" ::"v"(z) : "a232", "a233", "a234", "a235"); break;
-    case 59: asm volatile("v_accvgpr_write_b32 a236, %0\n\tv_accvgpr_write_b32 a237, %0\n\tv_accvgpr_write_b32 a238, %0\n\tv_accvgpr_write_b32 a239, %0" ::"v"(z) : "a236", "a237", "a238", "a239"); break;
-    case 60: asm volatile("v_accvgpr_write_b32 a240, %0\n\tv_accvgpr_write_b32 a241, %0\n\tv_accvgpr_write_b32 a242, %0\n\tv_accvgpr_write_b32 a243, %0" ::"v"(z) : "a240", "a241", "a242", "a243"); break;
-    case 61: asm volatile("v_accvgpr_write_b32 a244, %0\n\tv_accvgpr_write_b32 a245, %0\n\tv_accvgpr_write_b32 a246, %0\n\tv_accvgpr_write_b32 a247, %0" ::"v"(z) : "a244", "a245", "a246", "a247"); break;
-    case 62: asm volatile("v_accvgpr_write_b32 a248, %0\n\tv_accvgpr_write_b32 a249, %0\n\tv_accvgpr_write_b32 a250, %0\n\tv_accvgpr_write_b32 a251, %0" ::"v"(z) : "a248", "a249", "a250", "a251"); break;
-    case 63: asm volatile("v_accvgpr_write_b32 a252, %0\n\tv_accvgpr_write_b32 a253, %0\n\tv_accvgpr_write_b32 a254, %0\n\tv_accvgpr_write_b32 a255, %0" ::"v"(z) : "a252", "a253", "a254", "a255"); break;
   }
 }
 __device__ __forceinline__ f32x4 acc_read(int idx) {
@@ -553,18 +482,9 @@ inline int w4_grid_cap() {
 }
 template <int EPI>
 void launch_w4(const WideArgs& b, hipStream_t st) {
-  static const bool done = [&] {  // thread-safe one-time setup: two lane threads reach a kernel's first launch together
-    (void)hipFuncSetAttribute((const void*)gemm_wide256w4_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, W4_LDS);
-    return true;
-  }();
-  (void)done;
   const int ntiles = b.tilesM * b.tilesN, n = w4_grid_cap();
-  hipLaunchKernelGGL((gemm_wide256w4_kernel<EPI>), dim3(ntiles < n ? ntiles : n), dim3(256), W4_LDS, st, b);
+  launch_big_lds<gemm_wide256w4_kernel<EPI>>(dim3(ntiles < n ? ntiles : n), dim3(256), W4_LDS, st, b);
 }
-
-#ifdef HWOCR_DIAG
-#include "diag_src/gemm256w4_experiments.inc"  // measurement variants + cycle stamps (tools/bench_gemm_w4.py); never in the product library
-#endif
 
 }  // namespace
 
@@ -585,41 +505,5 @@ bool hwocr_gemm_wide256_w4(const gemm::WideArgs& b, int epi, bool forced, hipStr
                     (tiles + grid - 1) / grid, b.K >> 6);
     return true;
   }
-  switch (epi) {
-    case EPI_LINEAR: launch_w4<EPI_LINEAR>(b, st); return true;
-    case EPI_RESIDUAL: launch_w4<EPI_RESIDUAL>(b, st); return true;
-    case EPI_QUICKGELU: launch_w4<EPI_QUICKGELU>(b, st); return true;
-    case EPI_GELU: launch_w4<EPI_GELU>(b, st); return true;
-    case EPI_GELU_TANH: launch_w4<EPI_GELU_TANH>(b, st); return true;
-    case EPI_SWIGLU: launch_w4<EPI_SWIGLU>(b, st); return true;
-    case EPI_GEGLU: launch_w4<EPI_GEGLU>(b, st); return true;
-  }
-  return false;
+  return with_epilogue(WideEpis{}, epi, [&](auto e) { launch_w4<decltype(e)::value>(b, st); });
 }
-
-#ifdef HWOCR_DIAG
-
-// out[M][N] = bf16(X[M][K] . W[N][K]^T + bias); K % 64 == 0, N % 8 == 0 (diagnostic entry point, not in hwocr.h)
-extern "C" int hwocr_debug_gemm_w4(const void* X, const void* W, const void* bias, void* out, int M, int N, int K, hipStream_t stream) {
-  static const int abl = [] { const char* e = getenv("HWOCR_W4_ABLATE"); return e ? atoi(e) : 0; }();
-  (void)hipGetLastError();
-  if (!X || !W || !out || M <= 0 || N <= 0 || K < 128 || (K % 64) || (N % 8)) return HWOCR_EINVAL;
-  WideArgs a{(const bf16*)X, (const bf16*)W, (const bf16*)bias, nullptr, (bf16*)out, M, N, K, K, K, N, 0, (M + BM - 1) / BM, (N + BN - 1) / BN};
-  static const int form = [] { const char* e = getenv("HWOCR_W4_FORM"); return e ? atoi(e) : 16; }();
-  auto k32 = abl == 1 ? gemm_w4x32_kernel<1> : abl == 2 ? gemm_w4x32_kernel<2> : abl == 3 ? gemm_w4x32_kernel<3> : gemm_w4x32_kernel<0>;
-  auto k = form == 32 ? k32 : abl == 1 ? gemm_w4_kernel<1> : abl == 2 ? gemm_w4_kernel<2> : abl == 3 ? gemm_w4_kernel<3> : abl == 4 ? gemm_w4_kernel<4>
-           : abl == 6 ? gemm_w4_kernel<6> : gemm_w4_kernel<0>;
-  static const bool done = [&] {  // thread-safe one-time setup: two lane threads reach a kernel's first launch together
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    return true;
-  }();
-  (void)done;
-  hipLaunchKernelGGL(k, dim3(a.tilesM * a.tilesN), dim3(256), LDS_BYTES, stream, a);
-  return hwocr_launch_status();
-}
-// shader cycles / 100 MHz ticks of the main loop, per workgroup, of the last hwocr_debug_gemm_w4 launch
-extern "C" int hwocr_debug_gemm_w4_stamps(unsigned long long* host, int n) {
-  if (!host || n <= 0 || n > 2 * 8192) return HWOCR_EINVAL;
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_w4_stamps), sizeof(unsigned long long) * n) == hipSuccess ? HWOCR_OK : HWOCR_ELAUNCH;
-}
-#endif  // HWOCR_DIAG

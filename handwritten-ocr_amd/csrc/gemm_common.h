@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "hwocr.h"
+#include <type_traits>
 
 namespace gemm {
 
@@ -18,6 +19,26 @@ enum : int {
   EPI_VIT_QKV = 8                       // 256x256 kernel only (hwocr_gemm_vit_qkv): bias, vision rotary, head split, V transposed
 };
 template <int EPI> inline constexpr bool is_glu = EPI == EPI_SWIGLU || EPI == EPI_GEGLU;
+
+// ---- host side: from a run-time epilogue code to a kernel instance.  with_epilogue calls f(std::integral_constant<int, E>{}) for the
+// member E of the launcher's set that equals epi; false (nothing called) for a code outside the set.
+template <int... E> struct EpiSet {};
+using WideEpis = EpiSet<EPI_LINEAR, EPI_RESIDUAL, EPI_QUICKGELU, EPI_GELU, EPI_SWIGLU, EPI_GELU_TANH, EPI_GEGLU>;
+template <int... E, typename F>
+inline bool with_epilogue(EpiSet<E...>, int epi, F&& f) {
+  return ((epi == E ? (f(std::integral_constant<int, E>{}), true) : false) || ...);
+}
+// Launch of a kernel instance whose dynamic LDS exceeds the default limit: the attribute is set once per instance, thread-safe (two
+// lane threads reach a kernel's first launch together).
+template <auto KERNEL, typename ARGS>
+inline void launch_big_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const ARGS& args) {
+  static const bool done = [&] {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    return true;
+  }();
+  (void)done;
+  hipLaunchKernelGGL(KERNEL, grid, block, lds, st, args);
+}
 
 // The activations run once per output element in the GEMM epilogues (128 elements per lane and tile), so their instruction
 // count is tile time: an IEEE fp32 division is ~10 VALU instructions and tanhf ~40; here a sigmoid is exp + rcp (v_exp_f32,

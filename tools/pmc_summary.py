@@ -15,7 +15,8 @@ import sys
 
 
 def key(name: str) -> str:
-    if re.search(r"gemm_wide256_kernel<\d+, (true|false), true", name):  # the E4M3 instances (<EPI, STAGGER, FP8, ...>)
+    # the E4M3 instances: <EPI, FP8>; traces recorded up to 0de058f carry two more parameters (<EPI, true, FP8, 0>)
+    if re.search(r"gemm_wide256_kernel<\d+, (true>|(true|false), true, \d+>)", name):
         return "gemm_wide256_kernel_fp8"
     if "gemm_wide256w4_kernel" in name:  # the four-wave form of the same GEMM: one family for the traffic figure bench.py reads
         return "gemm_wide256_kernel"
